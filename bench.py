@@ -12,8 +12,10 @@ N > 1 (one process per GPU, torchrun): strong scaling -- ONE SCOP40-shaped set, 
 target lies in its range of the triangle (ranges balanced by DP cells), value = all cells / max-over-ranks time;
 the only exchange is an RCCL all_gather of the per-rank hit buffers.  The whole `-search` call is sharded the same
 way (`search`).  --weak gives every rank an independent set instead.
-Beside the contract's fields the line carries `roofline_live` (the kernels the live -search path runs) and
-`search_bca` (whole call from a .bca file, with the reference binary timed on this box's host cores).
+A plain run sets up, warms up, times --steps steps and prints the line (`roofline` from the last timed launch).  --full adds
+everything else: the untimed roofline passes, the reference CPU baseline, `roofline_live` (the kernels the live -search path
+runs), `search_bca` (whole call from a .bca file, with the reference binary timed on this box's host cores), predicted scaling,
+configs[2..4], the N > 1 gather check, and the detail record.  --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import json
@@ -976,6 +978,50 @@ def emit_detail(res, path):
     return res
 
 
+DUMP_SCORE_PAIRS = 8 << 20        # float32: at most 32 MB of the dense matrix
+DUMP_HIT_ROWS = 1 << 20           # float64 x 3: at most 24 MB of hit records
+DUMP_SEED = 0x5EED0D
+
+
+def triangle_sample(n, k, seed=DUMP_SEED):
+    """(i, j) with i <= j of an n x n matrix in row-major order: every pair when there are at most k, else the distinct pairs of k
+    seeded draws"""
+    npairs = n * (n + 1) // 2
+    if npairs <= k:
+        lin = np.arange(npairs, dtype=np.int64)
+    else:
+        lin = np.unique(np.random.default_rng(seed).integers(0, npairs, k, dtype=np.int64))
+    starts = np.concatenate(([0], np.cumsum(np.arange(n, 0, -1, dtype=np.int64))))     # starts[i]: linear index of (i, i)
+    i = np.searchsorted(starts, lin, side="right") - 1
+    return i, i + (lin - starts[i])
+
+
+def dump_outputs(path, out, n, hit_rows, windowed, dist, coll_dev, rank):
+    """What the timed path handed back in its last step -> path/*.npy (rank 0 writes; every rank takes part in the reduction).
+    N > 1 windows: a rank writes only its window's cells of the zeroed matrix, so the whole matrix is the maximum over ranks;
+    hit_rows are the records gathered from every rank."""
+    import torch
+    i, j = triangle_sample(n, DUMP_SCORE_PAIRS)
+    flat = torch.from_numpy(i * n + j).to(out.device)
+    vals = out.view(-1)[flat].to(torch.int32) & 0xFFFF             # uint16 scores held in an int16 tensor
+    if windowed:
+        vals = vals.to(coll_dev)
+        dist.all_reduce(vals, op=dist.ReduceOp.MAX)
+    if rank != 0:
+        return
+    rows = (hit_rows.cpu().numpy() if hasattr(hit_rows, "cpu") else np.asarray(hit_rows)).astype(np.int64).reshape(-1, 3)
+    count = len(rows)
+    rows = rows[np.lexsort((rows[:, 2], rows[:, 1], rows[:, 0]))]    # the kernel appends in no fixed order
+    if count > DUMP_HIT_ROWS:
+        rows = rows[np.sort(np.random.default_rng(DUMP_SEED).choice(count, DUMP_HIT_ROWS, replace=False))]
+    arrays = {"scores": vals.cpu().numpy().astype(np.float32), "hits": rows.astype(np.float64),
+              "hit_count": np.array([count], np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -1021,8 +1067,17 @@ def main():
     ap.add_argument("--configs-only", default="", help="only these legs, e.g. config3,config4 (prints their JSON and exits)")
     ap.add_argument("--search-scaling-only", action="store_true", help="only predicted_scaling.search (prints its JSON and exits)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"), help="where the full record goes (the last "
-                    "stdout line is the compact < 4 KB contract line)")
+                    "stdout line is the compact < 4 KB contract line); --full only")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the untimed roofline passes, the reference CPU "
+                    "baseline, predicted scaling, live-path rooflines, the end-to-end search legs, configs[2..4], the N > 1 gather check, "
+                    "the box record and the detail record; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last one computed as DIR/*.npy: "
+                    "scores.npy (float32 scores of the pairs i <= j of the dense matrix, row-major; a fixed seeded sample of %d draws "
+                    "when there are more), hits.npy (float64 [n, 3] hit records {query, target, score}, sorted; a seeded sample of %d "
+                    "rows when there are more), hit_count.npy" % (DUMP_SCORE_PAIRS, DUMP_HIT_ROWS))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)                     # does not return
@@ -1102,6 +1157,7 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
+    gathered = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -1119,16 +1175,21 @@ def main():
         summary[0] = gathered.shape[0]
     barrier()
     dt = time.perf_counter() - t0
-    # per-launch kernel time (the library's HIP events on the launch stream) and work of this rank's launches, untimed pass
-    step()
-    torch.cuda.synchronize()
+    if args.dump_outputs:
+        hit_rows = gathered if dist is not None else rec[:min(int(cnt[0].item()), HIT_CAP)]
+        dump_outputs(args.dump_outputs, out, n, hit_rows, windowed, dist, coll_dev, rank)
+    if args.full:
+        # per-launch kernel time and work of this rank's launches from an untimed pass
+        step()
+        torch.cuda.synchronize()
+    # the library's HIP events on the launch stream and its work counters: of the last launch (without --full the last timed step)
     kernel_ms = ctx.last_kernel_ms()
     pairs, cells, slots = ctx.mu_gapless_last_work()
     hits_rank = int(cnt[0].item())
 
     # the same pass without the dense matrix (hit records only: what a search needs), untimed, for the record
     kernel_ms_hits_only = None
-    if not windowed:
+    if not windowed and args.full:
         ctx.mu_gapless_hits_dev(db, db, True, HIT_MIN, rec.data_ptr(), HIT_CAP, cnt.data_ptr())
         torch.cuda.synchronize()
         kernel_ms_hits_only = ctx.last_kernel_ms()
@@ -1144,7 +1205,7 @@ def main():
     # (VERDICT r04 #3c).  Rank 0 scores the whole triangle once more, untimed, and compares the counts; the per-rank counts
     # must add up to the gathered total as well.
     gather_check = None
-    if dist is not None and windowed:
+    if dist is not None and windowed and args.full:
         hsum = torch.tensor([float(hits_rank)], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(hsum, op=dist.ReduceOp.SUM)
         if rank == 0:
@@ -1155,7 +1216,7 @@ def main():
             assert gather_check["gathered_all_ranks"] == one_gpu_hits == gather_check["sum_of_rank_counts"], \
                 "sharded hit records differ from the one-GPU triangle: %s" % gather_check
     search_n = None
-    if dist is not None and not args.no_search and not args.weak:
+    if dist is not None and args.full and not args.no_search and not args.weak:
         search_n = search_sharded_leg(ctx, seqs, rank, world, dist, coll_dev)
 
     if rank == 0:
@@ -1227,15 +1288,17 @@ def main():
                         "algorithmic_bytes": alg_bytes, "traffic": traffic},
                 "traffic": traffic, "traffic_source": traffic_src},
         }
-        res["box"] = box_info()
-        if not args.no_cpu_baseline and world == 1:
+        full = args.full                           # the legs below: --full only
+        if full:
+            res["box"] = box_info()
+        if full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(seqs)
-        if world == 1 and not args.chains and not args.no_predict:
+        if full and world == 1 and not args.chains and not args.no_predict:
             try:
                 res["predicted_scaling"] = predicted_scaling(ctx, seqs)
             except Exception as e:  # noqa: BLE001 -- the kernel metric above stands on its own
                 sys.stderr.write("bench: predicted-scaling leg failed: %s\n" % e)
-        if not args.no_live and world == 1 and not args.chains:
+        if full and not args.no_live and world == 1 and not args.chains:
             try:
                 del out
                 torch.cuda.empty_cache()
@@ -1244,7 +1307,7 @@ def main():
                 sys.stderr.write("bench: live-kernel leg failed: %s\n" % e)
         if search_n is not None:
             res["search"] = search_n
-        if world == 1:
+        if full and world == 1:
             # the legs below are whole searches on contexts of their own: give the kernel legs' device memory back first (the
             # pools of this context and of the parked helper contexts hold tens of GB of trace scratch)
             try:
@@ -1252,7 +1315,7 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as e:  # noqa: BLE001
                 sys.stderr.write("bench: trim failed: %s\n" % e)
-        if not args.no_search and world == 1 and not args.chains:
+        if full and not args.no_search and world == 1 and not args.chains:
             try:
                 res["search"] = search_end_to_end(seqs)
                 res["search_bca"] = search_vs_reference()
@@ -1263,12 +1326,13 @@ def main():
                     res.setdefault("predicted_scaling", {})["search"] = predicted_search_scaling(seqs)
                 except Exception as e:  # noqa: BLE001
                     sys.stderr.write("bench: predicted search-scaling leg failed: %s\n" % e)
-        if not args.no_configs and not args.no_search and world == 1 and not args.chains:
+        if full and not args.no_configs and not args.no_search and world == 1 and not args.chains:
             try:
                 res["configs"] = config_shares()
             except Exception as e:  # noqa: BLE001
                 sys.stderr.write("bench: configs[2..4] leg failed: %s\n" % e)
-        res = emit_detail(res, args.detail)
+        if full:
+            res = emit_detail(res, args.detail)
         final_line = compact_line(res)
     if dist is not None:
         dist.barrier()

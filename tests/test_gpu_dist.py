@@ -36,7 +36,7 @@ def test_search_sharded_world2_gloo_one_device():
 
 
 def test_bench_strong_scaling_world2_gloo_one_device():
-    r = _torchrun(os.path.join(ROOT, "bench.py"), 2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--chains", "1500"])
+    r = _torchrun(os.path.join(ROOT, "bench.py"), 2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--chains", "1500", "--full"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     res = json.loads(line)
@@ -65,7 +65,7 @@ def test_bench_gpus_2_spawns_its_own_ranks():
     env = dict(os.environ, RSK_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--chains", "1500", "--steps", "2"], capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--chains", "1500", "--steps", "2", "--full"], capture_output=True,
                        text=True, env=env, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     last = r.stdout.strip().splitlines()[-1]

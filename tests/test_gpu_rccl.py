@@ -40,7 +40,7 @@ def test_search_sharded_and_record_gather_over_rccl_world1():
 
 
 def test_bench_under_torchrun_world1_rccl():
-    r = _torchrun1(os.path.join(ROOT, "bench.py"), ["--gpus", "1", "--steps", "2", "--warmup", "1", "--chains", "1500", "--no-cpu-baseline"])
+    r = _torchrun1(os.path.join(ROOT, "bench.py"), ["--gpus", "1", "--steps", "2", "--warmup", "1", "--chains", "1500", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["config"]["collective_backend"] == "nccl"

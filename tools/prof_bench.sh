@@ -6,7 +6,7 @@ OUT=/tmp/rsk_prof/prof_$TAG
 KEEP=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT $KEEP
 export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-search --no-live --no-predict"
+CMD="python $(cd "$(dirname "$0")/.." && pwd)/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-search --no-live --no-predict"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $CMD > $OUT/trace.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT -d $OUT/pmc1 -o pmc -- $CMD > $OUT/pmc1.log 2>&1
